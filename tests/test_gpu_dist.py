@@ -4,7 +4,7 @@
   plain step and against ``oracle.adam_step``;
 * world 2 on ONE GPU (two processes, gloo through a pinned host copy): shard -> the product's forward/backward per rank -> dp_pack ->
   all-reduce -> fused Adam with the global count, against the same two shards run in one process and combined by hand;
-* world 2 over RCCL ("nccl") when the box has two GPUs (skipped otherwise);
+* world 2 over RCCL ("nccl"): one rank per GPU when the box has two, both ranks on cuda:0 otherwise;
 * the fault word: a set word makes the fused Adam skip on the device and the trainer raise; out-of-range labels set it; an
   empty shard yields zero gradients, not NaN.
 """
@@ -173,14 +173,21 @@ def test_empty_shard_contributes_zero_gradient(O):
 def _dp_worker(rank, world, port, backend, out_path, d_r, Bg, Ln):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       HSA_ENABLE_IPC_MODE_LEGACY="0")
+    import datetime
     import torch.distributed as dist
     ndev = torch.cuda.device_count()
     dev = torch.device("cuda", rank % ndev)
     torch.cuda.set_device(dev)
+    if backend == "nccl" and ndev < world:
+        # RCCL refuses two ranks on one device of one host ("Duplicate GPU detected").  A host id of its own per rank makes RCCL
+        # treat them as two one-GPU nodes joined by its socket transport (loopback): the collectives still reduce the device buffers
+        # with RCCL's kernels, only the hop between the ranks goes through host memory instead of P2P / shared memory.
+        os.environ.update(NCCL_HOSTID=f"mser-test-rank{rank}", NCCL_SOCKET_IFNAME="lo", NCCL_IB_DISABLE="1")
+    limit = datetime.timedelta(minutes=3)                # a collective that never completes ends the worker instead of the suite
     if backend == "nccl":
-        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev, timeout=limit)
     else:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
+        dist.init_process_group("gloo", rank=rank, world_size=world, timeout=limit)
     from oracle import ref_cpu as O
     from model_trainer import ModelTrainer
     from mser.dist import shard_batch
@@ -202,8 +209,14 @@ def _dp_worker(rank, world, port, backend, out_path, d_r, Bg, Ln):
         tr.train_step(xs, qs, us, ls)
     torch.cuda.synchronize()
     flat = tr.model.flat_store.data.detach().cpu()
-    gathered = [torch.zeros_like(flat) for _ in range(world)]
-    dist.all_gather(gathered, flat)
+    if backend == "nccl":                                # (an RCCL group moves device tensors only)
+        flat_d = tr.model.flat_store.data.detach().clone()
+        gathered = [torch.zeros_like(flat_d) for _ in range(world)]
+        dist.all_gather(gathered, flat_d)
+        gathered = [g.cpu() for g in gathered]
+    else:
+        gathered = [torch.zeros_like(flat) for _ in range(world)]
+        dist.all_gather(gathered, flat)
     # ---- a fault on ONE rank must raise on EVERY rank (train_network and eval_network decide collectively); rank 1 plants
     # a bad-label bit in its fault word, rank 0's word stays clean
     from mser import fault
@@ -299,8 +312,8 @@ def test_data_parallel_two_ranks_one_gpu_gloo(O, tmp_path):
 
 
 def test_data_parallel_two_ranks_rccl(O, tmp_path):
-    if torch.cuda.device_count() < 2:
-        pytest.skip("needs two GPUs (the driver's multi-GPU tier); the one-GPU gloo test above covers the device path")
+    """The same two-rank step over RCCL ("nccl"): FlatAllReduce reducing the device buffer in place, the replica broadcast and the
+    fault agreement on device tensors.  One rank per GPU where there are two; otherwise both share cuda:0 (see _dp_worker)."""
     _run_two_ranks(O, tmp_path, "nccl")
 
 
