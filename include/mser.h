@@ -22,7 +22,7 @@ extern "C" {
 
 typedef void* mser_stream_t; /* hipStream_t */
 
-#define MSER_VERSION 120   /* 110: + encoder layer, grouped GEMM, head tail, ingest, confusion, cell desc addends */
+#define MSER_VERSION 121   /* 121: + attention pool (mser_attn_pool_*); 110: + encoder layer, grouped GEMM, head tail, ingest, confusion, cell desc addends */
 
 int mser_version(void);
 const char* mser_last_error(void);
@@ -539,6 +539,50 @@ int mser_drnn_alpha(const mser_drnn_desc* d, int32_t dir, const float** alpha);
  * scores S0 as well. */
 int mser_general2_rows_fwd(const float* S0, float* alpha, const float* mask, int64_t rows, int32_t n, int32_t L, mser_stream_t stream);
 int mser_general2_rows_bwd(const float* S0, const float* mask, float* dA, int64_t rows, int32_t n, int32_t L, mser_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Attention pool of SimpleAttention (model/DialogueRNN.py:6-22) and MatchingAttention (:24-77) as standalone modules: the score,
+ * softmax and pool stages and their backward over a memory M[j, b, 0..D) (j < S <= MSER_ATTN_POOL_MAX_S; row j of batch b at
+ * M + j*sMj + b*sMb, unit inner stride).  Each pass is three launches sized to the whole S*B memory (a wave per memory row, a
+ * workgroup per batch row for the softmax, a wave per 64 features and batch row), not one workgroup per batch row.  The products
+ * with the modules' weights (W x, W_M M, W_x x, their weight and input gradients) are the caller's mser_gemm calls.
+ *   SIMPLE    s[b,j] = q . M[j,b]            q = scalar.weight (sqb = 0)                        softmax over j
+ *   DOT       s[b,j] = q[b] . M[j,b]         q = x                                             softmax over j
+ *   GENERAL   s[b,j] = q[b] . M[j,b]         q = W x                                           softmax over j
+ *   GENERAL2  s[b,j] = (q[b] . M[j,b]) m[b,j] q = W x + bias      a = softmax(s); alpha = a m / sum_j a m  (:61-67)
+ *   CONCAT    s[b,j] = v . tanh(A[j*B+b] + xb[b])   A = W_M M rows, xb = W_x x (W = [W_M | W_x])   softmax over j
+ * alpha [B, S], pool [B, D] = sum_j alpha[b,j] M[j,b].  The mask is read by GENERAL2 only (the reference ignores it elsewhere);
+ * NULL means ones.
+ * Backward from dpool (and, optionally, the gradient of alpha itself): ds [B, S] receives the score gradient; dM [S, B, D]
+ * contiguous, WRITTEN (alpha dpool + ds q; for CONCAT alpha dpool only -- the caller accumulates dA W_M); non-CONCAT: dq [B, D] =
+ * sum_j ds[b,j] M[j,b] (SIMPLE: the caller sums the rows into d scalar.weight); CONCAT: dA [S*B, Da] (row stride lda) =
+ * ds v (1 - t^2), dxb [B, Da] = sum_j of those rows, dvb [B, Da] = sum_j ds t (the caller sums the rows into
+ * d vector_prod.weight), t = tanh(A + xb).  B <= 65535.
+ * ------------------------------------------------------------------------------------------------ */
+enum { MSER_ATT_SIMPLE = 0, MSER_ATT_DOT = 1, MSER_ATT_GENERAL = 2, MSER_ATT_GENERAL2 = 3, MSER_ATT_CONCAT = 4 };
+#define MSER_ATTN_POOL_MAX_S 4096
+typedef struct mser_attn_pool_desc {
+  int32_t type, S, B, D;
+  const float* M; int64_t sMj, sMb;
+  const float* q; int64_t sqb;        /* non-CONCAT: score query of row b at q + b*sqb */
+  const float* mask;                  /* [B, S] or NULL (GENERAL2 only) */
+  int32_t Da;                         /* CONCAT: alpha_dim */
+  const float* A; int64_t lda;        /* CONCAT: [S*B, Da], row j*B + b */
+  const float* xb;                    /* CONCAT: [B, Da] */
+  const float* v;                     /* CONCAT: [Da] */
+  float* alpha;                       /* [B, S]: written by the forward, read by the backward */
+  float* pool;                        /* [B, D] */
+  /* backward */
+  const float* dpool;                 /* [B, D] */
+  const float* dalpha;                /* [B, S] or NULL */
+  float* dM;                          /* [S, B, D] */
+  float* dq;                          /* [B, D] (non-CONCAT) */
+  float* dA; float* dxb; float* dvb;  /* CONCAT: [S*B, Da] (row stride lda), [B, Da], [B, Da] */
+  float* ds;                          /* [B, S] score gradient (written) */
+} mser_attn_pool_desc;
+
+int mser_attn_pool_fwd(const mser_attn_pool_desc* d, mser_stream_t stream);
+int mser_attn_pool_bwd(const mser_attn_pool_desc* d, mser_stream_t stream);
 
 /* Dropout.  A site's mask is a pure function of (rng[0] = seed, rng[1] = step, site, element index): nothing is stored between
  * the forward and the backward, both evaluate keep(idx) = mix32(idx ^ key(seed, step, site)) >= p * 2^32 (a full-avalanche

@@ -1,38 +1,69 @@
 """MI355X-native mirror of the reference's ``models.DialogueRNN`` on the path the trainers use (reference file
-model/DialogueRNN.py; SURVEY.md 8(f) row f2, BASELINE configs[3]): ``MatchingAttention`` (:24-77, the 'general' and 'general2'
-types), ``DialogueRNNCell`` (:80-166), ``DialogueRNN`` (:169-198) and ``BiModel`` (:201-277) with the reference's constructor
-signatures, parameter names, shapes, registration order and initialisers (``state_dict`` files interchange).  ``BiModel.forward``
+model/DialogueRNN.py; SURVEY.md 8(f) row f2, BASELINE configs[3]): ``SimpleAttention`` (:6-22) and ``MatchingAttention`` (:24-77,
+all four types, standalone autograd nodes over csrc/attnpool.hip), ``DialogueRNNCell`` (:80-166), ``DialogueRNN`` (:169-198) and
+``BiModel`` (:201-277) with the reference's constructor signatures, parameter names, shapes, registration order and initialisers (``state_dict`` files interchange).  ``BiModel.forward``
 is ONE autograd node whose forward / backward are the kernel sequences of ``mser.bimodel_fn`` (HIP only).  The cell and the
 single-direction ``DialogueRNN`` hold the parameters in the reference's layout; their arithmetic runs inside ``BiModel`` (both
-directions share every launch).  Of the reference's other variants only what BiModel constructs is mirrored: 'simple' / 'dot' /
-'concat' attention, listener_state=False and the E2E / AVEC / DailyDialogue models are outside the hot path.
+directions share every launch).  Of the reference's other variants only what BiModel constructs is mirrored inside the cell:
+'simple' / 'dot' / 'concat' cell attention, listener_state=False and the E2E / AVEC / DailyDialogue models are outside the hot path.
 """
 import torch
 import torch.nn as nn
 
 from mser import ops
+from mser.attn_pool_fn import attn_pool
 from mser.autograd import require_gpu
 from mser.bimodel_fn import BiDims, BiDrop, bimodel_alpha_dir, bimodel_backward, bimodel_forward
 from mser.flat import FlatStore
 
 
+class SimpleAttention(nn.Module):
+    """Reference :6-22.  forward(M [S, B, D], x=None) -> (attn_pool [B, D], alpha [B, 1, S]): alpha = softmax_j(scalar(M_j)).
+    One autograd node (mser.attn_pool_fn: csrc/attnpool.hip for the score, softmax and pool stages)."""
+
+    def __init__(self, input_dim):
+        super(SimpleAttention, self).__init__()
+        self.input_dim = input_dim
+        self.scalar = nn.Linear(self.input_dim, 1, bias=False)
+
+    def forward(self, M, x=None):
+        require_gpu(M)
+        return attn_pool("simple", M, None, None, self.scalar.weight)
+
+
 class MatchingAttention(nn.Module):
-    """Reference :24-77.  Parameter holder for the types BiModel uses ('general': transform without bias; 'general2': with bias)."""
+    """Reference :24-77, all four types with the reference's parameters and registration order.  forward(M [S, B, mem_dim],
+    x [B, cand_dim], mask [B, S] = None) -> (attn_pool [B, mem_dim], alpha [B, 1, S]) is one autograd node (mser.attn_pool_fn);
+    as in the reference only 'general2' reads the mask.  Inside BiModel the 'general' cell attention and the 'general2' head
+    attention run in the fused launches of mser.bimodel_fn instead."""
 
     def __init__(self, mem_dim, cand_dim, alpha_dim=None, att_type='general'):
         super(MatchingAttention, self).__init__()
         assert att_type != 'concat' or alpha_dim is not None
         assert att_type != 'dot' or mem_dim == cand_dim
-        if att_type not in ('general', 'general2'):
-            raise NotImplementedError(f"MatchingAttention att_type '{att_type}' is outside the accelerated path (BiModel uses 'general' "
-                                      "inside the cell and 'general2' over the emotion states)")
         self.mem_dim = mem_dim
         self.cand_dim = cand_dim
         self.att_type = att_type
-        self.transform = nn.Linear(cand_dim, mem_dim, bias=(att_type == 'general2'))
+        if att_type == 'general':
+            self.transform = nn.Linear(cand_dim, mem_dim, bias=False)
+        if att_type == 'general2':
+            self.transform = nn.Linear(cand_dim, mem_dim, bias=True)
+        elif att_type == 'concat':
+            self.transform = nn.Linear(cand_dim + mem_dim, alpha_dim, bias=False)
+            self.vector_prod = nn.Linear(alpha_dim, 1, bias=False)
 
     def forward(self, M, x, mask=None):
-        raise NotImplementedError("models.DialogueRNN.MatchingAttention runs inside BiModel (mser.bimodel_fn)")
+        t = self.att_type
+        require_gpu(M, x, mask if t == 'general2' else None)        # the other types never read the mask (as in the reference)
+        if t == 'dot':
+            return attn_pool(t, M, x, None, None)
+        if t == 'general':
+            return attn_pool(t, M, x, None, self.transform.weight)
+        if t == 'general2':
+            return attn_pool(t, M, x, mask, self.transform.weight, self.transform.bias)
+        if t == 'concat':
+            return attn_pool(t, M, x, None, self.transform.weight, None, self.vector_prod.weight)
+        raise ValueError(f"MatchingAttention: unknown att_type '{t}' (the reference knows 'dot', 'general', 'general2', 'concat')")
 
 
 class DialogueRNNCell(nn.Module):

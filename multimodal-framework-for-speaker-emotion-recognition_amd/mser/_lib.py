@@ -130,6 +130,18 @@ class HeadTailDesc(C.Structure):
                 ("rng", C.c_void_p), ("site_out", C.c_uint32), ("p_out", C.c_float), ("p_fc", C.c_float)]
 
 
+class AttnPoolDesc(C.Structure):
+    """mser_attn_pool_desc (include/mser.h)."""
+    _fields_ = [("type", C.c_int32), ("S", C.c_int32), ("B", C.c_int32), ("D", C.c_int32),
+                ("M", C.c_void_p), ("sMj", C.c_int64), ("sMb", C.c_int64), ("q", C.c_void_p), ("sqb", C.c_int64),
+                ("mask", C.c_void_p), ("Da", C.c_int32), ("A", C.c_void_p), ("lda", C.c_int64), ("xb", C.c_void_p),
+                ("v", C.c_void_p), ("alpha", C.c_void_p), ("pool", C.c_void_p),
+                ("dpool", C.c_void_p), ("dalpha", C.c_void_p), ("dM", C.c_void_p), ("dq", C.c_void_p),
+                ("dA", C.c_void_p), ("dxb", C.c_void_p), ("dvb", C.c_void_p), ("ds", C.c_void_p)]
+
+
+MSER_ATT_SIMPLE, MSER_ATT_DOT, MSER_ATT_GENERAL, MSER_ATT_GENERAL2, MSER_ATT_CONCAT = 0, 1, 2, 3, 4
+MSER_ATTN_POOL_MAX_S = 4096
 MSER_GEMM_RELU = 1
 MSER_GEMM_ACCUM = 2
 MSER_FAULT_CHAIN_TIMEOUT, MSER_FAULT_LINK_TIMEOUT, MSER_FAULT_BAD_LABEL = 1, 2, 4
@@ -199,6 +211,8 @@ SIGNATURES = {
     "mser_drnn_alpha": (C.c_int, [C.POINTER(DrnnDesc), _i32, C.POINTER(C.c_void_p)]),
     "mser_general2_rows_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "mser_general2_rows_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
+    "mser_attn_pool_fwd": (C.c_int, [C.POINTER(AttnPoolDesc), _vp]),
+    "mser_attn_pool_bwd": (C.c_int, [C.POINTER(AttnPoolDesc), _vp]),
     "mser_set_option": (C.c_int, [_i32, _i32]),
     "mser_marn_cell_status": (C.c_int, [C.POINTER(CellDesc), _vp]),
     "mser_prof_enable": (C.c_int, [_i32, _i32]),
